@@ -17,6 +17,12 @@ GPU and host-core slice: GOP-level frame parallelism with no data-path collectiv
 segments exchange nothing), weak scaling.  The frame-level shard inside one encoder (frame encoder i on
 device session i mod G, X265AMD_GPUS) is exercised by the tests, not timed here.
 
+A run without --full does what `value` needs and no more: it writes the clip, encodes it once with the plain
+reference (the bitstream every step is checked against), warms up, times the K steps, writes the last
+step's bitstream with --dump-outputs DIR, and prints the line.  `roofline` and `encoder` below come from the
+last timed step's own counters; `cpu_baseline`, the second of `resolutions` and `primitive_workload` take
+runs of their own and are measured with --full (null or absent without it).
+
 Also reported (rank 0):
   roofline      — the dominant kernel of the encode, the batched motion search (k_motion_search): its
                   algorithmic bytes per launch (per full-pel evaluation 2 W H b, per sub-pel
@@ -78,6 +84,13 @@ def parse():
                          "`resolutions`; --second-res 0 0 skips it)")
     ap.add_argument("--host-rehearsal", action="store_true",
                     help="tests only: the hooks' host forms, no GPU (rank plumbing), value null")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: cpu_baseline (and its one-core sample), the second "
+                         "resolution, the primitive-workload replay.  Without it the run sets up, warms up, times "
+                         "the steps (each bitstream checked against the reference's) and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one produced to DIR/<name>.npy (rank 0): the "
+                         "bitstream's bytes as float32 (a fixed seeded sample of a longer one) and its length")
     return ap.parse_args()
 
 
@@ -161,19 +174,30 @@ def cpu_model() -> str:
 
 def write_clip(path, w, h, depth, first, n):
     """frames first .. first + n - 1 of the synthetic sequence (a closed segment of rank r: first = n r)"""
+    import concurrent.futures as cf
+
     import numpy as np
 
     from src.x265_amd.synth import SyntheticSource
 
     src = SyntheticSource(w, h, first + n, depth)
-    with open(path, "wb") as f:
-        for i in range(first, first + n):
-            for plane in src.frame(i):
-                f.write(plane.astype("<u2" if depth > 8 else np.uint8).tobytes())
+    dt = "<u2" if depth > 8 else np.uint8
+
+    def frame_bytes(i):
+        return b"".join(plane.astype(dt).tobytes() for plane in src.frame(i))
+
+    # a frame depends on its index alone (its own seeded noise): generated a rank's core share at a time,
+    # written in order
+    jobs = max(1, min(CORES_PER_GPU, len(os.sched_getaffinity(0))))
+    with open(path, "wb") as f, cf.ThreadPoolExecutor(jobs) as ex:
+        for lo in range(first, first + n, jobs):
+            for data in ex.map(frame_bytes, range(lo, min(lo + jobs, first + n))):
+                f.write(data)
 
 
-def x265_run(exe, src, w, h, depth, frames, extra, env=None, cpus=None, timeout=900):
-    """One encode; returns (x265's fps, wall seconds, bitstream md5, stderr)."""
+def x265_run(exe, src, w, h, depth, frames, extra, env=None, cpus=None, timeout=900, keep=None):
+    """One encode; returns (x265's fps, wall seconds, bitstream md5, stderr).  keep = a list: it receives the
+    bitstream's bytes (--dump-outputs)."""
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "o.hevc")
         cmd = [exe, "--input", src, "--input-res", f"{w}x{h}", "--input-depth", str(depth), "--fps", "30",
@@ -187,8 +211,11 @@ def x265_run(exe, src, w, h, depth, frames, extra, env=None, cpus=None, timeout=
         if r.returncode != 0:
             raise RuntimeError(f"{os.path.basename(exe)} rc={r.returncode}: {r.stderr[-800:]}")
         m = re.search(r"encoded (\d+) frames in ([\d.]+)s \(([\d.]+) fps\)", r.stderr)
-        md5 = hashlib.md5(open(out, "rb").read()).hexdigest()
-        return float(m.group(3)), wall, md5, r.stderr
+        with open(out, "rb") as f:
+            data = f.read()
+        if keep is not None:
+            keep[:] = [data]
+        return float(m.group(3)), wall, hashlib.md5(data).hexdigest(), r.stderr
 
 
 def parse_me_stats(err: str):
@@ -268,10 +295,27 @@ def me_roofline(st, traffic_file=ME_TRAFFIC):
                      "latency-bound: one workgroup of up to four waves per search, ~7 searches per launch); " + tbasis}
 
 
-def run_arm(args, world, rank, la, ref, W, H, F, D, cpus, extra, env, ref_env, steps, warmup, tag):
+DUMP_MAX_VALUES = 15 << 20     # float32 values of the bitstream in a dump: 60 MiB
+
+
+def dump_outputs(out_dir, bitstream: bytes):
+    """--dump-outputs: what the last timed step handed its caller, the encoded bitstream — its bytes as
+    float32 (of a longer one the bytes at a fixed seeded choice of positions, in order) and its length"""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    b = np.frombuffer(bitstream, np.uint8)
+    if b.size > DUMP_MAX_VALUES:
+        b = b[np.sort(np.random.default_rng(20261019).choice(b.size, DUMP_MAX_VALUES, replace=False))]
+    np.save(os.path.join(out_dir, "bitstream.npy"), b.astype(np.float32))
+    np.save(os.path.join(out_dir, "bitstream_bytes.npy"), np.array([len(bitstream)], np.float64))
+
+
+def run_arm(args, world, rank, la, ref, W, H, F, D, cpus, extra, env, ref_env, steps, warmup, tag, keep=None):
     """one resolution: this rank's segment clip, the plain reference's bitstream (and fps) on it, `warmup`
     untimed and `steps` timed hooked encodes (bracketed by barriers; the elapsed time is the max over
-    ranks), every bitstream compared with the reference's"""
+    ranks), every bitstream compared with the reference's; keep = a list: it receives the last timed
+    step's bitstream"""
     with tempfile.TemporaryDirectory(prefix=f"bench{rank}_{tag}_") as td:
         src = os.path.join(td, "clip.yuv")
         progress(f"rank {rank} [{tag}]: writing frames {F * rank}..{F * rank + F - 1} ({W}x{H} {D}-bit)")
@@ -293,7 +337,8 @@ def run_arm(args, world, rank, la, ref, W, H, F, D, cpus, extra, env, ref_env, s
         runs, walls, err = [], [], ""
         t0 = time.perf_counter()
         for i in range(steps):
-            f, wall, m, err = x265_run(la, src, W, H, D, F, extra, env=env, cpus=cpus)
+            last = {"keep": keep} if keep is not None and i == steps - 1 else {}
+            f, wall, m, err = x265_run(la, src, W, H, D, F, extra, env=env, cpus=cpus, **last)
             mismatches += m != ref_md5
             runs.append(f)
             walls.append(wall)
@@ -303,7 +348,8 @@ def run_arm(args, world, rank, la, ref, W, H, F, D, cpus, extra, env, ref_env, s
         elapsed = max_over_ranks(elapsed, world)
         identical = all_true(mismatches == 0, world)
         one_core = None
-        if rank == 0 and world == 1 and not args.no_cpu and D == 8 and tag == "2160p" and not args.host_rehearsal:
+        if (args.full and rank == 0 and world == 1 and not args.no_cpu and D == 8 and tag == "2160p"
+                and not args.host_rehearsal):
             n1 = 2
             f1, _, _, _ = x265_run(ref, src, W, H, D, n1, ["--preset", args.preset, "--pools", "1", "-F", "1"],
                                    cpus=cpus[:1])
@@ -312,6 +358,24 @@ def run_arm(args, world, rank, la, ref, W, H, F, D, cpus, extra, env, ref_env, s
     return {"fps": fps, "elapsed": elapsed, "identical": identical, "mismatching_encodes_this_rank": mismatches,
             "runs": runs, "walls": walls, "err": err, "ref_fps": ref_fps, "ref_wall": ref_wall, "one_core": one_core,
             "W": W, "H": H, "F": F, "steps": steps}
+
+
+def device_check(local: int) -> str:
+    """the rank's GPU, asked of the product library the hooked encoder runs on (src/x265_amd/libx265amd.so,
+    loaded here as the encoder loads it): no library or no device is an error, there is no CPU fallback.
+    Returns the gfx target the library was compiled for."""
+    import ctypes
+
+    from src.x265_amd import Primitives, X265AmdError
+
+    try:
+        lib = Primitives().lib
+    except (X265AmdError, OSError) as e:
+        raise SystemExit(f"bench.py: {e}")
+    n = ctypes.c_int(0)
+    if lib.x265amd_device_count(ctypes.byref(n)) != 0 or n.value <= local:
+        raise SystemExit("bench.py needs the MI355X (no CPU fallback)")
+    return lib.x265amd_target().decode()
 
 
 def main():
@@ -324,11 +388,9 @@ def main():
     ref = os.path.join(ROOT, "oracle", "_ref", "x265ref8")
     if not os.path.exists(la):
         raise SystemExit(f"{la} missing (build with __graft_entry__.build())")
+    target = None
     if not args.host_rehearsal:
-        import torch
-
-        if not torch.cuda.is_available():
-            raise SystemExit("bench.py needs the MI355X (no CPU fallback)")
+        target = device_check(local)
     cpus = core_slice(local, world)
     pools = str(len(cpus))
     extra = ["--preset", args.preset, "--pools", pools]
@@ -348,15 +410,18 @@ def main():
     env.update(kv.split("=", 1) for kv in args.env)
     ref_env = dict(os.environ, X265AMD_LOOKAHEAD="cpu", X265AMD_ME="cpu")
 
+    kept = [] if args.dump_outputs and rank == 0 else None
     head = run_arm(args, world, rank, la, ref, W, H, F, D, cpus, extra, env, ref_env, args.steps, args.warmup,
-                   f"{H}p")
+                   f"{H}p", keep=kept)
+    if kept:
+        dump_outputs(args.dump_outputs, kept[0])
     second = None
-    if args.second_res[0] > 0 and (args.second_res[0], args.second_res[1]) != (W, H):
+    if args.full and args.second_res[0] > 0 and (args.second_res[0], args.second_res[1]) != (W, H):
         w2, h2 = args.second_res
         second = run_arm(args, world, rank, la, ref, w2, h2, F, D, cpus, extra, env, ref_env, args.steps, 1,
                          f"{h2}p")
     replay = None
-    if rank == 0 and world == 1 and not args.no_replay and not args.host_rehearsal:
+    if args.full and rank == 0 and world == 1 and not args.no_replay and not args.host_rehearsal:
         progress("primitive-workload replay (1080p census)")
         try:
             from src.x265_amd.replay_bench import primitive_workload
@@ -377,14 +442,18 @@ def main():
     st = parse_me_stats(head["err"])
     ms_per_step = head["elapsed"] * 1000.0 / args.steps
 
+    def speedup(a):
+        # the reference encode of a run without --full is the bitstream check alone, not a baseline
+        return round(statistics.median(a["runs"]) / a["ref_fps"], 3) if args.full else None
+
     def arm_summary(a):
         sm = {"fps": round(a["fps"], 3), "mpix_per_s": round(a["fps"] * a["W"] * a["H"] / 1e6, 1),
               "resolution": f"{a['W']}x{a['H']}", "frames_per_step_per_gpu": a["F"], "steps": a["steps"],
               "timed_region_s": round(a["elapsed"], 3), "bitstreams_identical_to_reference": a["identical"],
               "fps_runs": a["runs"], "wall_s_runs": [round(w, 3) for w in a["walls"]],
-              "speedup_vs_reference_same_cores": round(statistics.median(a["runs"]) / a["ref_fps"], 3),
+              "speedup_vs_reference_same_cores": speedup(a),
               "device_path": parse_me_stats(a["err"])}
-        if world == 1:
+        if world == 1 and args.full:
             sm["cpu_baseline"] = {"value": a["ref_fps"], "unit": "fps", "cores": len(cpus), "kind": "reference",
                                   "wall_s": round(a["ref_wall"], 3),
                                   "mpix_per_s": round(a["ref_fps"] * a["W"] * a["H"] / 1e6, 2)}
@@ -420,7 +489,7 @@ def main():
                    "resolution": f"{W}x{H}", "depth": D, "frames_per_step_per_gpu": F, "preset": args.preset,
                    "parallelism": f"GOP shard x{world}: rank r encodes the closed segment of frames {F}r..{F}r+{F - 1} "
                                   "on its own GPU and host-core slice; no data-path collective (DESIGN.md §6)",
-                   "host_cores_per_gpu": len(cpus), "cpu_model": cpu_model(),
+                   "host_cores_per_gpu": len(cpus), "cpu_model": cpu_model(), "library_target": target,
                    "hooked_env": {k: v for k, v in env.items() if k.startswith("X265AMD")}},
         "mpix_per_s": round(head["fps"] * W * H / 1e6, 1) if identical else None,
         "timed_region_s": round(head["elapsed"], 3),
@@ -436,8 +505,8 @@ def main():
                                    f"sources; no asm) encoding the same {F}-frame clip on the same {len(cpus)} cores "
                                    "(--pools), one run", "wall_s": round(head["ref_wall"], 3),
                          "mpix_per_s": round(head["ref_fps"] * W * H / 1e6, 2),
-                         "one_core": head["one_core"]} if world == 1 else None,
-        "speedup_vs_reference_same_cores": round(statistics.median(head["runs"]) / head["ref_fps"], 3),
+                         "one_core": head["one_core"]} if world == 1 and args.full else None,
+        "speedup_vs_reference_same_cores": speedup(head),
         "primitive_workload": replay,
     }
     print(json.dumps(line), flush=True)

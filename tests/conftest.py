@@ -3,6 +3,17 @@ import sys
 
 import pytest
 
+# The HIP runtime page-locks pageable host memory itself for a host<->device copy of more than 1 MiB
+# (AMD_LOG_LEVEL=4: "HSA Copy Using Pinned resource"; up to 1 MiB: "Using Staging resource") and keeps the
+# last few such mappings to find them again by host address.  The GPU tests copy freshly allocated numpy /
+# torch host arrays of many MiB all the time: when one is freed (its pages unmapped) and a later one lands at
+# the same address, the copy can go through the kept mapping of pages the process no longer owns and faults
+# the device — "an illegal memory access" raised by a copy with no kernel in flight, which is how every
+# occurrence of the suite's intermittent fault looks.  With the threshold (MiB) above any test
+# buffer the runtime stages these copies through its own page-locked buffers instead.  Read when the runtime
+# loads, so it is set here, before anything imports torch; the encoders the tests start inherit it.
+os.environ.setdefault("GPU_PINNED_MIN_XFER_SIZE", "4096")
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
     if p not in sys.path:

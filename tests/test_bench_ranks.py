@@ -26,7 +26,7 @@ REF = os.path.join(ROOT, "oracle", "_ref", "x265ref8")
 def test_bench_two_ranks_host_rehearsal():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--frames", "5", "--width", "256", "--height", "144", "--second-res", "320", "192", "--host-rehearsal",
-           "--no-cpu", "--no-replay"]
+           "--no-cpu", "--no-replay", "--full"]     # (--full: the second resolution)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
