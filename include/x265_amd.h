@@ -38,7 +38,8 @@
 extern "C" {
 #endif
 
-/* 1: per-shape batched entries; 2: + the *_grouped multi-shape entries */
+/* 1: per-shape batched entries; 2: + the *_grouped multi-shape entries (additive since, version unchanged:
+ * x265amd_intra_costs, the fused intra mode-decision costs) */
 #define X265AMD_ABI_VERSION 2
 
 enum
@@ -236,6 +237,57 @@ int x265amd_intra_allangs(int depth, int size, int n,
                           const void* ref, const int64_t* ref_off,
                           const void* filt, const int64_t* filt_off,
                           const uint8_t* bluma, void* stream);
+
+/* ---------------------------------------------------------- a14 fused mode costs
+ * The intra mode decision of one luma PU in one kernel: from the source block and its UNFILTERED
+ * reconstructed neighbours to the 35 SA8D costs and the winning mode, bit-identical to
+ * search.cpp:1250-1343 + the full-search loop :1381-1388 (checkIntraInInter) and to
+ * search.cpp:1488-1558 (estIntraPredQT).  No prediction leaves the chip.  Per job:
+ *   - neighbour smoothing as Predict::initAdiPattern with ALL_IDX (predict.cpp:608-648): for
+ *     N = 8, 16, 32 the filtered buffer is intra_filter of nb; for N = 32 with strong_smoothing the
+ *     bilinear form when both threshold tests (1 << (depth - 5)) pass; N = 4 has none;
+ *   - log2_size 6: fenc is 64x64 and nb holds 257 pixels; the block goes through scale2D_64to32
+ *     and the neighbours through scale1D_128to64 (top-left kept), both neighbour buffers are the
+ *     scaled unfiltered one, prediction and SA8D run at 32x32 with bFilter 0 and sad <<= 2;
+ *   - DC from the unfiltered buffer with bFilter = (N <= 16); planar from the filtered buffer for
+ *     PUs 8..32; modes 2..34 from the buffer g_intraFilterFlags[mode] & N selects, the mode-10/26
+ *     edge filter at N <= 16 (all_angs_pred_c);
+ *   - sad[mode]  = cu[].sa8d(fenc, pred) << costShift (4x4: SATD, as the table aliases it);
+ *   - cost[mode] = sad + ((b * lambda + 128) >> 8) in 64 bits (RDCost::calcRdSADCost), b = bits[k]
+ *     for the first k with mpm[k] == mode, bits[3] (rbits) when none matches;
+ *   - best = the minimum in the reference's order with strict <: DC, planar, 2..34.
+ * Not covered: the sampled search of bEnableFastIntra (search.cpp:1345-1380, off at every preset
+ * up to slow) and estIntraPredQT's updateCandList top-k selection (a few host instructions over
+ * cost[]).
+ * The whole call is validated before any launch; X265AMD_EINVAL for a depth intra_pred rejects,
+ * log2_size outside 2..6, n < 0 or count < 0, n > 0 with fenc, nb or an offset array NULL, cost or
+ * best set while mpm, bits or lambda is NULL, and all three outputs NULL.  count == 0 and n == 0
+ * batches are no-ops.  Launches go to the caller's stream, one per non-empty batch. */
+typedef struct
+{
+    uint64_t cost;      /* calcRdSADCost of the winner */
+    uint32_t sad;       /* its sa8d << costShift (Mode::distortion) */
+    uint32_t bits;      /* its mode bits (Mode::sa8dBits) */
+    uint32_t mode;      /* 0 planar, 1 DC, 2..34 */
+    uint32_t reserved;  /* written 0 */
+} x265amd_intra_best;
+
+typedef struct
+{
+    int log2_size;            /* 2..5: PU 4x4..32x32; 6: the 64x64 form of checkIntraInInter */
+    int n;
+    int strong_smoothing;     /* sps.bUseStrongIntraSmoothing (acts at 32x32 only) */
+    const void* fenc; intptr_t fenc_stride; const int64_t* fenc_off;
+    const void* nb;   const int64_t* nb_off;    /* UNFILTERED neighbours, a14 layout, 4N+1 per job */
+    const uint8_t*  mpm;      /* 3 per job: mpmModes[0..2]; NULL = distortions only */
+    const uint32_t* bits;     /* 4 per job: bitsIntraModeMPM of mpm[0], mpm[1], mpm[2], then rbits */
+    const uint32_t* lambda;   /* 1 per job: RDCost::m_lambda */
+    int32_t*  sad;            /* 35 per job (index = mode), or NULL */
+    uint64_t* cost;           /* 35 per job, or NULL */
+    x265amd_intra_best* best; /* 1 per job, or NULL */
+} x265amd_intra_cost_batch;
+
+int x265amd_intra_costs(int depth, int count, const x265amd_intra_cost_batch* batches, void* stream);
 
 /* --------------------------------------------------------------------- a15
  * Companion block ops (pixel.cpp:338-436, 490-502, 705-808; dct.cpp:714-742).

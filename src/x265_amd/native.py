@@ -44,6 +44,17 @@ class TuBatch(C.Structure):
                 ("num_sig", _vp), ("qp", _vp), ("scan", _vp)]
 
 
+class IntraBest(C.Structure):
+    _fields_ = [("cost", C.c_uint64), ("sad", C.c_uint32), ("bits", C.c_uint32), ("mode", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class IntraCostBatch(C.Structure):
+    _fields_ = [("log2_size", _int), ("n", _int), ("strong_smoothing", _int), ("fenc", _vp), ("fenc_stride", _ip),
+                ("fenc_off", _vp), ("nb", _vp), ("nb_off", _vp), ("mpm", _vp), ("bits", _vp), ("lambda_", _vp),
+                ("sad", _vp), ("cost", _vp), ("best", _vp)]
+
+
 class LowresBatch(C.Structure):
     _fields_ = [("n", _int), ("width", _int), ("lines", _int), ("margin_x", _int), ("margin_y", _int),
                 ("src", _vp), ("src_stride", _ip), ("src_off", _vp), ("planes", _vp), ("lowres_stride", _ip),
@@ -184,6 +195,17 @@ def interp_batches(items):
     return arr
 
 
+def intra_cost_batches(items):
+    """items: (log2_size, strong, fenc, fs, foff, nb, nboff, mpm, bits, lam, sad, cost, best) with torch tensors
+    (mpm / bits / lam and any of the outputs may be None; best: 24 bytes per job, the IntraBest layout)
+    -> IntraCostBatch array"""
+    arr = (IntraCostBatch * len(items))()
+    for i, (log2, strong, f, fs, foff, nb, nboff, mpm, bits, lam, sad, cost, best) in enumerate(items):
+        arr[i] = IntraCostBatch(log2, foff.numel(), int(strong), _addr(f), fs, _addr(foff), _addr(nb), _addr(nboff),
+                                _addr(mpm), _addr(bits), _addr(lam), _addr(sad), _addr(cost), _addr(best))
+    return arr
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -272,6 +294,10 @@ class Primitives:
         self._check(self.lib.x265amd_intra_allangs(depth, size, doff.numel(), _ptr(d), _ptr(doff), _ptr(ref),
                                                    _ptr(roff), _ptr(filt), _ptr(foff), _ptr(bluma),
                                                    stream or _stream()), "intra_allangs")
+
+    # -- a14 fused mode costs: `arr` from intra_cost_batches
+    def intra_costs(self, depth, arr, stream=None):
+        self._check(self.lib.x265amd_intra_costs(depth, len(arr), arr, stream or _stream()), "intra_costs")
 
     # -- a15
     def blockop(self, op, depth, w, h, d, ds, doff, a, sa, aoff, b, sb, boff, param=0, stream=None):

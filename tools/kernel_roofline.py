@@ -744,7 +744,90 @@ def main():
             print(json.dumps(r), flush=True)
         del src, dst, du, stats, count
         torch.cuda.empty_cache()
+    # ---------------------------------------------------------------- fused intra mode costs
+    # (a) x265amd_intra_costs with all three outputs against (b) the same operation through the existing
+    # entries: intra_filter, intra_pred (DC, planar), intra_allangs, TRANSPOSE and 35 x pixelcmp(SA8D), on the
+    # same disjointly tiled source blocks and packed neighbour arrays.  The kernel is compute- and LDS-bound:
+    # beside the HBM fraction the row carries a VALU-side estimate, the Hadamard butterflies and |.| sums of the
+    # 35 differences alone (8-bit: two values per packed op) against the 78.6 T lane-ops/s of the vector units.
+    # Five repeats of each side, alternating; the spread is the run-to-run noise.
+    if want("intra_costs"):
+        from src.x265_amd.native import intra_cost_batches
+
+        VALU_PEAK = 78.6e12
+        TRANSPOSE_OP = 13
+        for s in (4, 8, 16, 32):
+            lg = {4: 2, 8: 3, 16: 4, 32: 5}[s]
+            nbn = 4 * s + 1
+            n = min(1 << 20, int(a.gb * 1e9 / (37 * s * s + 2 * nbn + 444)))
+            x, y, rows = tiled_offsets(n, s, s, s, s, W)
+            fenc = rand_u8(rows * W)
+            foff = torch.from_numpy(y * W + x).to(dev)
+            nb = rand_u8(n * nbn)
+            nboff = torch.arange(n, dtype=torch.int64, device=dev) * nbn
+            mpm = torch.tensor([0, 1, 26], dtype=torch.uint8, device=dev).repeat(n)
+            bits = torch.tensor([2, 3, 3, 6], dtype=torch.int32, device=dev).repeat(n)
+            lam = torch.full((n,), 1500, dtype=torch.int32, device=dev)
+            sad = torch.empty(n * 35, dtype=torch.int32, device=dev)
+            cost = torch.empty(n * 35, dtype=torch.int64, device=dev)
+            best = torch.empty(n * 3, dtype=torch.int64, device=dev)
+            arr = intra_cost_batches([(lg, 0, fenc, W, foff, nb, nboff, mpm, bits, lam, sad, cost, best)])
+
+            filt = torch.empty_like(nb)
+            pred = torch.empty(n * s * s, dtype=torch.uint8, device=dev)
+            fenc_t = torch.empty_like(pred)
+            angs = torch.empty(n * 33 * s * s, dtype=torch.uint8, device=dev)
+            poff = torch.arange(n, dtype=torch.int64, device=dev) * (s * s)
+            moff = [torch.arange(n, dtype=torch.int64, device=dev) * (33 * s * s) + m * s * s for m in range(33)]
+            mode_dc = torch.ones(n, dtype=torch.uint8, device=dev)
+            mode_pl = torch.zeros(n, dtype=torch.uint8, device=dev)
+            bf = torch.full((n,), 1 if s <= 16 else 0, dtype=torch.uint8, device=dev)
+            out = torch.empty(35 * n, dtype=torch.int32, device=dev)
+            pl_src = filt if s >= 8 else nb
+
+            def fused():
+                prims.intra_costs(8, arr)
+
+            def chain():
+                if s >= 8:
+                    prims.intra_filter(8, s, nb, nboff, filt, nboff)
+                prims.intra_pred(8, s, pred, s, poff, nb, nboff, mode_dc, bf)
+                prims.pixelcmp(SA8D, 8, s, s, fenc, W, foff, pred, s, poff, out[n:2 * n])
+                prims.intra_pred(8, s, pred, s, poff, pl_src, nboff, mode_pl, mode_pl)
+                prims.pixelcmp(SA8D, 8, s, s, fenc, W, foff, pred, s, poff, out[0:n])
+                prims.blockop(TRANSPOSE_OP, 8, s, s, fenc_t, s, poff, fenc, W, foff, fenc, W, foff)
+                prims.intra_allangs(8, s, angs, moff[0], nb, nboff, pl_src, nboff, bf)
+                for m in range(2, 35):
+                    if m < 18:
+                        prims.pixelcmp(SA8D, 8, s, s, fenc_t, s, poff, angs, s, moff[m - 2], out[m * n:(m + 1) * n])
+                    else:
+                        prims.pixelcmp(SA8D, 8, s, s, fenc, W, foff, angs, s, moff[m - 2], out[m * n:(m + 1) * n])
+
+            fa, ch = [], []
+            for _ in range(5):
+                fa.append(timeit(fused))
+                ch.append(timeit(chain))
+            # the two sides computed the same distortions (the chain's out is mode-major)
+            same = bool(torch.equal(sad.view(n, 35).t().contiguous().view(-1), out))
+            ms_a, ms_b = sum(fa) / 5, sum(ch) / 5
+            bytes_job = s * s + nbn + 35 * 4 + 35 * 8 + 24
+            had_ops = 35 * ((s // 8) ** 2 * (6 * 64 + 128) // 2 if s >= 8 else 4 * 16 + 32)
+            r = {"kernel": f"intra_costs_{s}x{s}", "jobs": n, "bound": "compute (VALU) and LDS, not HBM",
+                 "fused_ms": round(ms_a, 4), "fused_ms_spread": [round(min(fa), 4), round(max(fa), 4)],
+                 "unfused_chain_ms": round(ms_b, 4), "unfused_ms_spread": [round(min(ch), 4), round(max(ch), 4)],
+                 "unfused_launches": 39 if s >= 8 else 38, "ratio_unfused_over_fused": round(ms_b / ms_a, 2),
+                 "fused_jobs_per_s": round(n / (ms_a * 1e-3), 1), "unfused_jobs_per_s": round(n / (ms_b * 1e-3), 1),
+                 "algorithmic_bytes_per_job": bytes_job,
+                 "frac_of_8TBps": round(n * bytes_job / (ms_a * 1e-3) / 1e9 / HBM, 4),
+                 "hadamard_lane_ops_per_job": had_ops,
+                 "valu_frac_hadamard_only": round(n * had_ops / (ms_a * 1e-3) / VALU_PEAK, 4),
+                 "outputs_equal": same}
+            results.append(r)
+            print(json.dumps(r), flush=True)
+            del fenc, nb, filt, pred, fenc_t, angs, moff, out, sad, cost, best
+            torch.cuda.empty_cache()
     if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump({"hbm_peak_GBps": HBM, "working_set_GB": a.gb, "results": results}, f, indent=1)
 
