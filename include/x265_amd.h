@@ -39,7 +39,8 @@ extern "C" {
 #endif
 
 /* 1: per-shape batched entries; 2: + the *_grouped multi-shape entries (additive since, version unchanged:
- * x265amd_intra_costs, the fused intra mode-decision costs) */
+ * x265amd_intra_costs, the fused intra mode-decision costs; x265amd_inter_costs, the fused merge / bidir
+ * candidate costs) */
 #define X265AMD_ABI_VERSION 2
 
 enum
@@ -925,6 +926,88 @@ typedef struct
     double batch_hist_ms[5];
 } x265amd_mes_counters;
 int x265amd_mes_stats(x265amd_mes* mes, x265amd_mes_counters* out);
+
+/* ---------------------------------------------------------- f2 fused candidate costs
+ * The evaluation of up to K candidate motions of one 2Nx2N inter CU in one kernel: motion compensation
+ * of every candidate, its SA8D distortion against the source, calcRdSADCost, the winner and the
+ * winner's prediction, bit-identical to the candidate loop of Analysis::checkMerge2Nx2N_rd0_4
+ * (analysis.cpp:1689-1724) and to the two estimates of Analysis::checkBidir2Nx2N (analysis.cpp:2013-2140).
+ * No intermediate and no prediction but the winner's leaves the chip.  The three uses:
+ *   merge   the merge candidates in slot order, dir = candDir, bits = getTUBits(i, numMergeCand);
+ *   bidir   K = 2: slot 0 = direction 3 with the best L0 / L1 MVs, slot 1 = direction 3 with both MVs
+ *           zero.  The zero-MV candidate is the coincident-block estimate: its luma equals
+ *           pixelavg_pp(fref0, fref1), because addAvg of two convert_p2s planes reduces to
+ *           (a + b + 1) >> 1 at every depth.  Bidir callers take sad[] and form
+ *           sa8d + getCost(bits) themselves;
+ *   plain   K = 1 with pred: fused motion compensation of one PU.
+ * Per candidate k of job i (slot = i * K + k):
+ *   - dir 0: the slot is not evaluated (the frame-parallel and intra-refresh skips); 1: list 0;
+ *     2: list 1; 3: both.  Only the low two bits are read.
+ *   - luma, one list: Predict::predInterLumaPixel (predict.cpp:251-272) on ref + ref_off[slot * 2 + l]:
+ *     frac = mv & 3, integer offset = mv >> 2; frac (0, 0) copy_pp, (x, 0) luma_hpp, (0, y) luma_vpp,
+ *     (x, y) luma_hvpp (luma_hps with row extension, then the sp vertical form);
+ *   - luma, two lists: Predict::predInterLumaShort (predict.cpp:274-305) per list: convert_p2s, luma_hps,
+ *     luma_vps, or luma_hps with row extension followed by luma_vss; then addAvg (pixel.cpp:789-808):
+ *     clip((a + b + offset) >> shiftNum), shiftNum = IF_INTERNAL_PREC + 1 - depth,
+ *     offset = (1 << (shiftNum - 1)) + 2 * IF_INTERNAL_OFFS;
+ *   - chroma (4:2:0, when the six chroma inputs are given = m_bChromaSa8d): predInterChromaPixel /
+ *     predInterChromaShort (predict.cpp:307-407): frac = mv & 7 = coeffIdx, offset = mv >> 3, the 4-tap
+ *     filters; 2-D uni = filter_hps with row extension + filter_vsp, 2-D bi = filter_hps with row
+ *     extension + filter_vss; Cb and Cr use the same offsets ref_coff[slot * 2 + l];
+ *   - sad[slot] = primitives.cu[log2_size - 2].sa8d(fenc, pred), plus with chroma
+ *     chroma[I420].cu[].sa8d of Cb and of Cr (CU 8: SATD 4x4; 16: sa8d8<8,8>; 32: sa8d16<16,16>;
+ *     64: sa8d16<32,32>), each with the 8x8 / 16x16 rounding units of pixel.cpp:244-322
+ *     (analysis.cpp:1711-1716);
+ *   - cost[slot] = sad + ((bits * lambda + 128) >> 8) in 64 bits (RDCost::calcRdSADCost);
+ *   - best = the first strict minimum of cost over the live slots in slot order, starting from
+ *     INT64_MAX (analysis.cpp:1717-1723).  With no live slot: cost INT64_MAX, cand -1, sad and bits 0;
+ *   - pred / pred_cb / pred_cr receive the winner's prediction (bestPred->predYuv), N x N (N/2 x N/2)
+ *     pixels at pred_off[i] (pred_coff[i]) and nothing else; untouched for a CU with no live slot.
+ * Read contract: per list the kernel reads only what the reference chain reads: N x N at the integer
+ * offset, 3 pixels before and 4 after on an axis only when that axis has a fraction (chroma: 1 and
+ * 2).  Reference planes are border-extended as PicYuv is; mv is ALREADY clipped (CUData::clipMv).
+ * Not covered, the caller keeps such candidates on the host: weighted prediction (addWeightUni /
+ * addWeightBi), 4:2:2 / 4:4:4 chroma, non-2Nx2N PUs, MV clipping and candidate derivation.
+ * The whole call is validated before any launch; X265AMD_EINVAL for a depth x265amd_interp rejects,
+ * log2_size outside 3..6, max_cand outside 1..5, n < 0 or count < 0, n > 0 with fenc, ref, dir, mv or
+ * the offset array of a given plane NULL, a partial chroma set (some of the six chroma inputs, or some
+ * of pred_cb / pred_cr / pred_coff; pred_cb without the chroma inputs or without pred), cost, best or
+ * pred set while bits or lambda is NULL, and every output NULL.  count == 0 and n == 0 batches are
+ * no-ops.  Launches go to the caller's stream, one per non-empty batch. */
+typedef struct
+{
+    uint64_t cost;      /* calcRdSADCost of the winner; INT64_MAX when no candidate is live */
+    uint32_t sad;       /* its distortion (Mode::distortion): luma sa8d, + Cb + Cr when chroma is given */
+    uint32_t bits;      /* its bits[] entry */
+    int32_t  cand;      /* its candidate slot (bestSadCand), -1 when none is live */
+    uint32_t reserved;  /* written 0 */
+} x265amd_inter_best;   /* 24 bytes */
+
+typedef struct
+{
+    int log2_size;            /* 3..6: CU 8x8..64x64 */
+    int n;                    /* CUs */
+    int max_cand;             /* K, 1..5 (MRG_MAX_NUM_CANDS) candidate slots per CU */
+    const void* fenc; intptr_t fenc_stride; const int64_t* fenc_off;      /* n */
+    const void* ref;  intptr_t ref_stride;  const int64_t* ref_off;       /* n*K*2: the CU's co-located origin in the
+                                                  luma plane of list l's picture for candidate k, [(i*K + k)*2 + l] */
+    const uint8_t*  dir;      /* n*K: 0 = slot not evaluated, 1 = L0, 2 = L1, 3 = bi (candDir / interDir) */
+    const int16_t*  mv;       /* n*K*2*2: (x, y) quarter-pel per list, ALREADY clipped (CUData::clipMv) */
+    const uint32_t* bits;     /* n*K: sa8dBits of the candidate; NULL = distortions only */
+    const uint32_t* lambda;   /* n: RDCost::m_lambda */
+    /* 4:2:0 chroma, all NULL = luma only (m_bChromaSa8d off) */
+    const void* fenc_cb; const void* fenc_cr; intptr_t fenc_cstride; const int64_t* fenc_coff;   /* n */
+    const void* ref_cb;  const void* ref_cr;  intptr_t ref_cstride;  const int64_t* ref_coff;    /* n*K*2 */
+    uint32_t* sad;            /* n*K or NULL; a dir-0 slot gets 0xFFFFFFFF */
+    uint64_t* cost;           /* n*K or NULL; a dir-0 slot gets UINT64_MAX */
+    x265amd_inter_best* best; /* n or NULL */
+    /* the winner's prediction (what bestPred->predYuv holds), or NULL; untouched for a CU with no live candidate */
+    void* pred; intptr_t pred_stride; const int64_t* pred_off;                                    /* n */
+    void* pred_cb; void* pred_cr; intptr_t pred_cstride; const int64_t* pred_coff;                /* n */
+} x265amd_inter_cost_batch;
+
+int x265amd_inter_costs(int depth, int count, const x265amd_inter_cost_batch* batches, void* stream);
+
 /* ------------------------------------------------------------------- f3 in the running encoder
  * Inter residual coding session (round 6; csrc/rdosession.cpp, hook integration/gpu_rdo.cpp): the
  * transform units of an inter CU as Search::encodeResAndCalcRdInterCU -> estimateResidualQT

@@ -3,5 +3,5 @@
 The product is the C-ABI shared library libx265amd.so (include/x265_amd.h)
 built from csrc/*.hip; this package only builds and binds it.
 """
-from .native import (LIB_PATH, IntraBest, IntraCostBatch, Primitives, X265AmdError, capture_graph,  # noqa: F401
-                     intra_cost_batches)
+from .native import (LIB_PATH, InterBest, InterCostBatch, IntraBest, IntraCostBatch, Primitives,  # noqa: F401
+                     X265AmdError, capture_graph, inter_cost_batches, intra_cost_batches)

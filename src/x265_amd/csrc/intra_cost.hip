@@ -28,27 +28,6 @@ namespace x265amd {
 
 #include "hadamard.h"
 
-// raw 4x4 Hadamard |coef| sum (satd_4x4 before its >> 1)
-__device__ __forceinline__ uint32_t had4x4_raw(int (&d)[4][4])
-{
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-    {
-        const int t0 = d[i][0] + d[i][1], t1 = d[i][0] - d[i][1];
-        const int t2 = d[i][2] + d[i][3], t3 = d[i][2] - d[i][3];
-        d[i][0] = t0 + t2; d[i][2] = t0 - t2; d[i][1] = t1 + t3; d[i][3] = t1 - t3;
-    }
-    uint32_t s = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-    {
-        const int t0 = d[0][j] + d[1][j], t1 = d[0][j] - d[1][j];
-        const int t2 = d[2][j] + d[3][j], t3 = d[2][j] - d[3][j];
-        s += abs(t0 + t2) + abs(t0 - t2) + abs(t1 + t3) + abs(t1 - t3);
-    }
-    return s;
-}
-
 struct IntraCostArgs
 {
     int n, maxv, strong, threshold;

@@ -70,7 +70,7 @@ extern "C" int x265amd_sizeof(const char* type)
     T(x265amd_transfer) T(x265amd_propagate_batch) T(x265amd_weights_batch) T(x265amd_me_batch) T(x265amd_mes_config)
     T(x265amd_mes_job) T(x265amd_mes_counters) T(x265amd_sao_param) T(x265amd_sao_frame) T(x265amd_sao_stats_frame)
     T(x265amd_deblock_unit) T(x265amd_deblock_frame) T(x265amd_border_plane) T(x265amd_intra_cost_batch)
-    T(x265amd_intra_best)
+    T(x265amd_intra_best) T(x265amd_inter_cost_batch) T(x265amd_inter_best)
 #undef T
     return 0;
 }

@@ -55,6 +55,20 @@ class IntraCostBatch(C.Structure):
                 ("sad", _vp), ("cost", _vp), ("best", _vp)]
 
 
+class InterBest(C.Structure):
+    _fields_ = [("cost", C.c_uint64), ("sad", C.c_uint32), ("bits", C.c_uint32), ("cand", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
+class InterCostBatch(C.Structure):
+    _fields_ = [("log2_size", _int), ("n", _int), ("max_cand", _int), ("fenc", _vp), ("fenc_stride", _ip),
+                ("fenc_off", _vp), ("ref", _vp), ("ref_stride", _ip), ("ref_off", _vp), ("dir", _vp), ("mv", _vp),
+                ("bits", _vp), ("lambda_", _vp), ("fenc_cb", _vp), ("fenc_cr", _vp), ("fenc_cstride", _ip),
+                ("fenc_coff", _vp), ("ref_cb", _vp), ("ref_cr", _vp), ("ref_cstride", _ip), ("ref_coff", _vp),
+                ("sad", _vp), ("cost", _vp), ("best", _vp), ("pred", _vp), ("pred_stride", _ip), ("pred_off", _vp),
+                ("pred_cb", _vp), ("pred_cr", _vp), ("pred_cstride", _ip), ("pred_coff", _vp)]
+
+
 class LowresBatch(C.Structure):
     _fields_ = [("n", _int), ("width", _int), ("lines", _int), ("margin_x", _int), ("margin_y", _int),
                 ("src", _vp), ("src_stride", _ip), ("src_off", _vp), ("planes", _vp), ("lowres_stride", _ip),
@@ -206,6 +220,25 @@ def intra_cost_batches(items):
     return arr
 
 
+def inter_cost_batches(items):
+    """items: dicts with log2_size, max_cand, fenc, fenc_stride, fenc_off, ref, ref_stride, ref_off, dir, mv and
+    optionally bits, lam, the chroma inputs fenc_cb, fenc_cr, fenc_cstride, fenc_coff, ref_cb, ref_cr, ref_cstride,
+    ref_coff, the outputs sad, cost, best (24 bytes per CU, the InterBest layout) and pred, pred_stride, pred_off,
+    pred_cb, pred_cr, pred_cstride, pred_coff (torch tensors; a missing key is NULL / 0) -> InterCostBatch array"""
+    arr = (InterCostBatch * len(items))()
+    for i, it in enumerate(items):
+        g = it.get
+        arr[i] = InterCostBatch(
+            it["log2_size"], it["fenc_off"].numel(), it["max_cand"], _addr(it["fenc"]), it["fenc_stride"],
+            _addr(it["fenc_off"]), _addr(it["ref"]), it["ref_stride"], _addr(it["ref_off"]), _addr(it["dir"]),
+            _addr(it["mv"]), _addr(g("bits")), _addr(g("lam")), _addr(g("fenc_cb")), _addr(g("fenc_cr")),
+            g("fenc_cstride", 0), _addr(g("fenc_coff")), _addr(g("ref_cb")), _addr(g("ref_cr")), g("ref_cstride", 0),
+            _addr(g("ref_coff")), _addr(g("sad")), _addr(g("cost")), _addr(g("best")), _addr(g("pred")),
+            g("pred_stride", 0), _addr(g("pred_off")), _addr(g("pred_cb")), _addr(g("pred_cr")), g("pred_cstride", 0),
+            _addr(g("pred_coff")))
+    return arr
+
+
 def _ptr(t):
     if t is None:
         return None
@@ -298,6 +331,10 @@ class Primitives:
     # -- a14 fused mode costs: `arr` from intra_cost_batches
     def intra_costs(self, depth, arr, stream=None):
         self._check(self.lib.x265amd_intra_costs(depth, len(arr), arr, stream or _stream()), "intra_costs")
+
+    # -- f2 fused merge / bidir candidate costs: `arr` from inter_cost_batches
+    def inter_costs(self, depth, arr, stream=None):
+        self._check(self.lib.x265amd_inter_costs(depth, len(arr), arr, stream or _stream()), "inter_costs")
 
     # -- a15
     def blockop(self, op, depth, w, h, d, ds, doff, a, sa, aoff, b, sb, boff, param=0, stream=None):

@@ -826,6 +826,159 @@ def main():
             print(json.dumps(r), flush=True)
             del fenc, nb, filt, pred, fenc_t, angs, moff, out, sad, cost, best
             torch.cuda.empty_cache()
+    # ---------------------------------------------------------------- fused inter candidate costs
+    # (a) x265amd_inter_costs with all outputs (sad, cost, best and the winner's prediction) against (b) the same
+    # candidate evaluation through the existing entries on the same buffers: per slot and list the interpolation
+    # form its fractions select (COPY_PP / HPP / VPP / HVPP for uni; P2S / HPS / VPS / row-extended HPS + VSS
+    # for bi), ADDAVG for bi, and pixelcmp(SA8D) per plane.  Side (b) stops at the distortions: it has no
+    # cost / winner stage and does not copy the winner's prediction, which is in its favour.  5 slots per CU:
+    # slot 0 whole-pel, 1 horizontal, 2 vertical, 3 and 4 two-dimensional fractions (luma and chroma alike).
+    # Two mixes per size, 8 bit: uni, luma only; bi with 4:2:0 chroma (the medium preset's case).  Five
+    # repeats of each side, alternating; the spread is the run-to-run noise.
+    if want("inter_costs"):
+        from src.x265_amd.native import inter_cost_batches
+
+        P2S, ADDAVG_OP, COPY_PP_OP, K = 7, 2, 4, 5
+        rng = np.random.default_rng(265)
+        for s in (8, 16, 32, 64):
+            lg = {8: 3, 16: 4, 32: 5, 64: 6}[s]
+            m, pitch, marg = s // 2, s + 32, 48
+            n = min(1 << 19, int(a.gb * 1e9 / (3 * pitch * pitch + 2 * s * s)))
+            x, y, rows = tiled_offsets(n, s, s, pitch, pitch, W, marg)
+            pic, cpic, Wc = rows * W, (rows // 2) * (W // 2), W // 2
+            ref, ref_cb, ref_cr = rand_u8(2 * pic), rand_u8(2 * cpic), rand_u8(2 * cpic)
+            fx_, fy_, frows = tiled_offsets(n, s, s, s, s, W)
+            fenc, fenc_cb, fenc_cr = rand_u8(frows * W), rand_u8((frows // 2) * Wc), rand_u8((frows // 2) * Wc)
+            foff_h, fcoff_h = fy_ * W + fx_, (fy_ // 2) * Wc + fx_ // 2
+            # MVs: mv = 8 q + f8, f8 in {1, 2, 3, 5, 6, 7} on an axis with a fraction (luma and chroma both have one)
+            frac = np.array([1, 2, 3, 5, 6, 7])
+            hx = np.array([0, 1, 0, 1, 1])[None, :, None]
+            hy = np.array([0, 0, 1, 1, 1])[None, :, None]
+            mvx = 8 * rng.integers(-8, 9, (n, K, 2)) + hx * frac[rng.integers(0, 6, (n, K, 2))]
+            mvy = 8 * rng.integers(-8, 9, (n, K, 2)) + hy * frac[rng.integers(0, 6, (n, K, 2))]
+            mv_h = np.stack([mvx, mvy], axis=-1).astype(np.int16)
+            lst = np.arange(2)[None, None, :]
+            roff_h = (lst * pic + (y * W + x)[:, None, None]) + np.zeros((n, K, 2), np.int64)
+            rcoff_h = (lst * cpic + ((y // 2) * Wc + x // 2)[:, None, None]) + np.zeros((n, K, 2), np.int64)
+            T = lambda h: torch.from_numpy(np.ascontiguousarray(h)).to(dev)
+            foff, fcoff, roff, rcoff, mv = T(foff_h), T(fcoff_h), T(roff_h.reshape(-1)), T(rcoff_h.reshape(-1)), T(mv_h.reshape(-1))
+            bits = torch.randint(1, 12, (n * K,), dtype=torch.int32, device=dev)
+            lam = torch.full((n,), 1500, dtype=torch.int32, device=dev)
+            sad = torch.empty(n * K, dtype=torch.int32, device=dev)
+            cost = torch.empty(n * K, dtype=torch.int64, device=dev)
+            best = torch.empty(n * 3, dtype=torch.int64, device=dev)
+            pred, pred_cb, pred_cr = (torch.empty(n * s * s, dtype=torch.uint8, device=dev),
+                                      torch.empty(n * m * m, dtype=torch.uint8, device=dev),
+                                      torch.empty(n * m * m, dtype=torch.uint8, device=dev))
+            poff = torch.arange(n, dtype=torch.int64, device=dev) * (s * s)
+            pcoff = torch.arange(n, dtype=torch.int64, device=dev) * (m * m)
+            # side (b): per-slot operand offsets at the MV's integer part, coefficient indices, intermediates
+            so = [[T(roff_h[:, k, l] + (mvy[:, k, l] >> 2) * W + (mvx[:, k, l] >> 2)) for l in range(2)] for k in range(K)]
+            sco = [[T(rcoff_h[:, k, l] + (mvy[:, k, l] >> 3) * Wc + (mvx[:, k, l] >> 3)) for l in range(2)] for k in range(K)]
+            cxl = [[T((mvx[:, k, l] & 3).astype(np.uint8)) for l in range(2)] for k in range(K)]
+            cyl = [[T((mvy[:, k, l] & 3).astype(np.uint8)) for l in range(2)] for k in range(K)]
+            cxyl = [[T(((mvx[:, k, l] & 3) | ((mvy[:, k, l] & 3) << 4)).astype(np.uint8)) for l in range(2)] for k in range(K)]
+            cxc = [[T((mvx[:, k, l] & 7).astype(np.uint8)) for l in range(2)] for k in range(K)]
+            cyc = [[T((mvy[:, k, l] & 7).astype(np.uint8)) for l in range(2)] for k in range(K)]
+            sh = [[torch.empty(n * s * s, dtype=torch.int16, device=dev) for _ in range(2)],
+                  [torch.empty(n * m * m, dtype=torch.int16, device=dev) for _ in range(2)],
+                  [torch.empty(n * m * m, dtype=torch.int16, device=dev) for _ in range(2)]]
+            ext = torch.empty(n * (s + 7) * s, dtype=torch.int16, device=dev)
+            eoff = torch.arange(n, dtype=torch.int64, device=dev) * ((s + 7) * s)
+            ecoff = torch.arange(n, dtype=torch.int64, device=dev) * ((m + 3) * m)
+            eoff_v, ecoff_v = eoff + 3 * s, ecoff + m        # row taps / 2 - 1 of the row-extended image
+            out = [torch.empty(n * K, dtype=torch.int32, device=dev) for _ in range(3)]
+            dirs = {}
+
+            def item(bi):
+                it = dict(log2_size=lg, max_cand=K, fenc=fenc, fenc_stride=W, fenc_off=foff, ref=ref, ref_stride=W,
+                          ref_off=roff, dir=dirs[bi], mv=mv, bits=bits, lam=lam, sad=sad, cost=cost, best=best,
+                          pred=pred, pred_stride=s, pred_off=poff)
+                if bi:
+                    it.update(fenc_cb=fenc_cb, fenc_cr=fenc_cr, fenc_cstride=Wc, fenc_coff=fcoff, ref_cb=ref_cb,
+                              ref_cr=ref_cr, ref_cstride=Wc, ref_coff=rcoff, pred_cb=pred_cb, pred_cr=pred_cr,
+                              pred_cstride=m, pred_coff=pcoff)
+                return it
+
+            def short_form(k, l, taps, src, ss, soff, cx, cy, dst, w, xo):
+                """the int16 prediction of one list (predInter*Short) for slot k's case"""
+                if k == 0:
+                    prims.interp(P2S, taps, 8, w, w, src, ss, soff, dst, w, xo[0], cx)
+                elif k == 1:
+                    prims.interp(HPS, taps, 8, w, w, src, ss, soff, dst, w, xo[0], cx, 0)
+                elif k == 2:
+                    prims.interp(VPS, taps, 8, w, w, src, ss, soff, dst, w, xo[0], cy)
+                else:
+                    prims.interp(HPS, taps, 8, w, w, src, ss, soff, ext, w, xo[1], cx, 1)
+                    prims.interp(VSS, taps, 8, w, w, ext, w, xo[2], dst, w, xo[0], cy)
+
+            def chain_uni():
+                for k in range(K):
+                    if k == 0:
+                        prims.blockop(COPY_PP_OP, 8, s, s, pred, s, poff, ref, W, so[k][0], ref, W, so[k][0])
+                    elif k == 1:
+                        prims.interp(HPP, 8, 8, s, s, ref, W, so[k][0], pred, s, poff, cxl[k][0])
+                    elif k == 2:
+                        prims.interp(VPP, 8, 8, s, s, ref, W, so[k][0], pred, s, poff, cyl[k][0])
+                    else:
+                        prims.interp(HVPP, 8, 8, s, s, ref, W, so[k][0], pred, s, poff, cxyl[k][0])
+                    prims.pixelcmp(SA8D, 8, s, s, fenc, W, foff, pred, s, poff, out[0][k * n:(k + 1) * n])
+
+            def chain_bi():
+                for k in range(K):
+                    for l in range(2):
+                        short_form(k, l, 8, ref, W, so[k][l], cxl[k][l], cyl[k][l], sh[0][l], s, (poff, eoff, eoff_v))
+                        short_form(k, l, 4, ref_cb, Wc, sco[k][l], cxc[k][l], cyc[k][l], sh[1][l], m, (pcoff, ecoff, ecoff_v))
+                        short_form(k, l, 4, ref_cr, Wc, sco[k][l], cxc[k][l], cyc[k][l], sh[2][l], m, (pcoff, ecoff, ecoff_v))
+                    for p, (dst, w, xo, fe, fs, fo) in enumerate(((pred, s, poff, fenc, W, foff),
+                                                                   (pred_cb, m, pcoff, fenc_cb, Wc, fcoff),
+                                                                   (pred_cr, m, pcoff, fenc_cr, Wc, fcoff))):
+                        prims.blockop(ADDAVG_OP, 8, w, w, dst, w, xo, sh[p][0], w, xo, sh[p][1], w, xo)
+                        prims.pixelcmp(SA8D, 8, w, w, fe, fs, fo, dst, w, xo, out[p][k * n:(k + 1) * n])
+
+            for bi in (0, 1):
+                dirs[bi] = torch.full((n * K,), 3 if bi else 1, dtype=torch.uint8, device=dev)
+                arr = inter_cost_batches([item(bi)])
+
+                def fused():
+                    prims.inter_costs(8, arr)
+
+                chain = chain_bi if bi else chain_uni
+                fa, ch = [], []
+                for _ in range(5):
+                    fa.append(timeit(fused))
+                    ch.append(timeit(chain))
+                # the two sides computed the same distortions (the chain's out is slot-major)
+                fused()
+                chain()
+                torch.cuda.synchronize()
+                total = out[0] + out[1] + out[2] if bi else out[0]
+                same = bool(torch.equal(sad.view(n, K).t().contiguous().view(-1), total))
+                ms_a, ms_b = sum(fa) / 5, sum(ch) / 5
+                # algorithmic bytes of the fused entry: source block, the reference footprints of every slot and
+                # list (widened by taps - 1 on an axis with a fraction), descriptors, outputs, winner's prediction
+                nl = 2 if bi else 1
+                foot = sum((s + 7 * int(hx[0, k, 0])) * (s + 7 * int(hy[0, k, 0])) for k in range(K)) * nl
+                if bi:
+                    foot += 2 * sum((m + 3 * int(hx[0, k, 0])) * (m + 3 * int(hy[0, k, 0])) for k in range(K)) * nl
+                planes = s * s + (2 * m * m if bi else 0)
+                bytes_job = 2 * planes + foot + K * (1 + 8 + 4 + 16 + 4 + 8) + 8 + 4 + 24 + (32 if bi else 16)
+                launches = sum((2 * 3 * (2 if k >= 3 else 1) + 6) for k in range(K)) if bi else 2 * K
+                r = {"kernel": f"inter_costs_{s}x{s}_{'bi_chroma' if bi else 'uni_luma'}", "jobs": n, "slots": K,
+                     "bound": "compute (VALU) and LDS, not HBM",
+                     "fused_ms": round(ms_a, 4), "fused_ms_spread": [round(min(fa), 4), round(max(fa), 4)],
+                     "unfused_chain_ms": round(ms_b, 4), "unfused_ms_spread": [round(min(ch), 4), round(max(ch), 4)],
+                     "unfused_launches": launches, "ratio_unfused_over_fused": round(ms_b / ms_a, 2),
+                     "faster_beyond_spreads": bool(ms_b - ms_a > (max(fa) - min(fa)) + (max(ch) - min(ch))),
+                     "fused_jobs_per_s": round(n / (ms_a * 1e-3), 1), "unfused_jobs_per_s": round(n / (ms_b * 1e-3), 1),
+                     "algorithmic_bytes_per_job": bytes_job,
+                     "frac_of_8TBps": round(n * bytes_job / (ms_a * 1e-3) / 1e9 / HBM, 4),
+                     "outputs_equal": same}
+                results.append(r)
+                print(json.dumps(r), flush=True)
+            del ref, ref_cb, ref_cr, fenc, fenc_cb, fenc_cr, sh, ext, out, pred, pred_cb, pred_cr, sad, cost, best
+            del so, sco, cxl, cyl, cxyl, cxc, cyc
+            torch.cuda.empty_cache()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
